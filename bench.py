@@ -31,6 +31,8 @@ full record goes out one line earlier, prefixed `BENCH_DETAIL `, and into gpurun
   cpu_baseline  (1 GPU) BASELINE config 1 (128 states x 6 probers; 128 queries x 10k docs L2 top-5)
                 and the reference's batch-1 call shape, torch-cpu and the C restatement, on this
                 box's host cores
+`--dump-outputs DIR` writes what the last timed step computed (search scores / ids, gate logits / probability sums /
+decisions) as DIR/<name>.npy, float32 or float64, so that two builds run with the same arguments compare file for file.
 `python bench.py --e2e [--gpus N]` times BASELINE config 5 instead (bench_e2e.py): the retrieve-decide loop around a
 Gemma-2B-shaped decoder, HIP path next to the reference's data path; its own JSON line, never the default.
 Other sizes are parity/diagnostic cases, e.g. BASELINE config 3:
@@ -127,7 +129,50 @@ def parse(argv=None):
                          "host memory; 0: round 5's loop - prag_gate_decide after `generate` has returned")
     ap.add_argument("--e2e-cpu-docs", type=int, default=200_000,
                     help="rows of the sub-corpus the reference-style path scans on the CPU")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed - the search's scores and ids, "
+                         "the gate's logits, probability sums and decisions (rank 0; the gate rows of every rank) - as "
+                         "DIR/<name>.npy in float32 / float64.  The inputs are seeded, so two builds run with the same "
+                         "arguments can be compared file for file")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.e2e:
+        ap.error("--dump-outputs writes the outputs of the default workload, not of --e2e")
+    return args
+
+
+# what --dump-outputs may write in all: larger arrays are replaced by a fixed, seeded sample of their rows
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: array} as out_dir/<name>.npy: float64 arrays as they are, other floating arrays as float32, integer
+    arrays (ids, decisions) as float64, exact below 2^53.  If the whole would exceed `limit` bytes, each array keeps
+    the same seeded sample of its leading-axis rows (sorted), and the row numbers go out as <name>_rows.npy.
+    Returns {file name: shape}."""
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if not np.issubdtype(a.dtype, np.number) or np.issubdtype(a.dtype, np.complexfloating):
+            raise TypeError(f"{name}: cannot dump dtype {a.dtype}")
+        conv[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype.kind == "f" and a.dtype != np.float64 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > limit:
+        frac = limit / (total + sum(8 * a.shape[0] for a in conv.values()))       # (+ the row numbers)
+        for name in list(conv):
+            n = conv[name].shape[0]
+            keep = max(1, int(n * frac))
+            if keep < n:
+                rows = np.sort(np.random.default_rng(20240611).choice(n, keep, replace=False))
+                conv[name] = np.ascontiguousarray(conv[name][rows])
+                conv[name + "_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1014,6 +1059,20 @@ def main(argv=None):
     ens.profile(0)
     fallbacks = local.last_exact_fallbacks()
     plan_timed = plan_summary(local.last_plan())        # the plan of the timed passes (later searches overwrite the record)
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's results, copied before any later search or gate reuses their buffers; the search's
+        # (D, I) are the merged lists (the same on every rank), the gate's rows are this rank's slice
+        gate_host = [t.cpu().numpy() for t in gate_out]
+        if world > 1:
+            slices = [None] * world
+            dist.all_gather_object(slices, gate_host)
+            gate_host = [np.concatenate([s[0] for s in slices], axis=1)] + \
+                        [np.concatenate([s[j] for s in slices], axis=0) for j in (1, 2)]
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {
+                "search_scores": D.cpu().numpy(), "search_ids": I.cpu().numpy(),
+                "gate_logits": gate_host[0], "gate_probsum": gate_host[1], "gate_decision": gate_host[2]})
     xch_ms = local.profile_read_exchange() if index.exchange == "prag_rccl" else []
     dt_rank = dt
     if world > 1:
@@ -1411,6 +1470,8 @@ def main(argv=None):
         out["cpu_baseline"] = cpu_baseline(args, states, q_c1, x_c1)
     else:
         out["cpu_baseline"] = None
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     emit(out, real_stdout)
     if world > 1:
         index.close()

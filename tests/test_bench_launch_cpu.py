@@ -216,3 +216,47 @@ def test_library_chatter_cannot_reach_stdout():
     assert out.returncode == 0, out.stderr
     assert out.stdout == '{"ok": true}\n'
     assert "[Gloo]" in out.stderr and "python chatter" in out.stderr
+
+
+# ---- --dump-outputs / --steps ----------------------------------------------------------------------------------
+def test_steps_below_one_and_dump_with_e2e_are_refused():
+    import pytest
+    import bench
+    assert bench.parse(["--steps", "3"]).steps == 3 and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--dump-outputs", "out"]).dump_outputs == "out"
+    for argv in (["--steps", "0"], ["--steps", "-2"], ["--e2e", "--dump-outputs", "out"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
+
+
+def test_dump_outputs_writes_float_npy_files_exactly(tmp_path):
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"search_scores": rng.standard_normal((64, 10)).astype(np.float32),
+              "search_ids": rng.integers(0, 21_000_000, (64, 10), dtype=np.int64),
+              "gate_logits": rng.standard_normal((6, 4096, 2)).astype(np.float32),
+              "gate_decision": rng.integers(0, 2, 4096, dtype=np.int32),
+              "f16": rng.standard_normal(5).astype(np.float16), "f64": rng.standard_normal(5)}
+    written = bench.dump_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(written) == sorted(n + ".npy" for n in arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "d" / (name + ".npy"))
+        assert got.dtype in (np.float32, np.float64) and got.shape == a.shape
+        assert np.array_equal(got, a.astype(got.dtype)) and np.array_equal(got.astype(a.dtype), a)
+    assert np.load(tmp_path / "d" / "search_ids.npy").dtype == np.float64
+
+
+def test_dump_outputs_samples_the_same_rows_every_time_beyond_the_limit(tmp_path):
+    import numpy as np
+    import bench
+    a = np.arange(40_000, dtype=np.float32).reshape(10_000, 4)
+    ids = np.arange(10_000, dtype=np.int64)
+    for d in ("x", "y"):
+        written = bench.dump_outputs(str(tmp_path / d), {"a": a, "ids": ids}, limit=64_000)
+        assert sum(np.load(tmp_path / d / f).nbytes for f in written) <= 64_000
+    rows = np.load(tmp_path / "x" / "a_rows.npy")
+    assert 0 < len(rows) < 10_000 and np.all(np.diff(rows) > 0)
+    for f in written:
+        assert np.array_equal(np.load(tmp_path / "x" / f), np.load(tmp_path / "y" / f))
+    assert np.array_equal(np.load(tmp_path / "x" / "a.npy"), a[rows.astype(np.int64)])
