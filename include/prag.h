@@ -300,6 +300,29 @@ int prag_index_d(const prag_index_t* ix);
 int prag_index_search(prag_index_t* ix, const float* q, int B, int k, int64_t id_offset,
                       float* D, int64_t* I, int io_is_device, void* stream);
 
+/* Exact range search (faiss `index.range_search(x, radius)`): every stored row within `radius` of each query.
+ *   s64(q, x) is the float64 score search ranks by (stored rows as kept - fp16-rounded for PRAG_F16 -, the fp32
+ *   query, normalised as search normalises it for COS).  L2: row i belongs to query b iff s64 < (double)radius;
+ *   IP / COS: iff s64 > (double)radius (strict, as faiss).
+ *   lims: int64 [B+1] in HOST memory - the call synchronises `stream`, since the sizes must be known; the results of
+ *   query b are entries [lims[b], lims[b+1]) in ASCENDING row id (deterministic), D = float32(s64), bit-identical to
+ *   the D search returns for the same row and query, I = row id + id_offset.
+ *   q: float32 [B,d], a device pointer if io_is_device, else a host pointer.  1 <= B <= 1024.  ntotal == 0 or no
+ *   row in range: lims all zero.  The results stay in the handle until the next range search or destroy
+ *   (prag_index_range_result).  The matrix-core scan only proposes candidates (every row whose selection key is
+ *   within the certificate's error bound of the radius); each is re-scored in float64.  PRAG_ENOMEM when the
+ *   candidates or results do not fit in device memory (the handle stays usable).  Not on the 8-bit shadow, not
+ *   capturable into a graph (it synchronises), no C-level sharded form: ShardedFlatIndex.range_search exchanges
+ *   the per-rank results through torch.distributed.  Leaves every state of search untouched. */
+int prag_index_range_search(prag_index_t* ix, const float* q, int B, float radius, int64_t id_offset,
+                            int64_t* lims, int io_is_device, void* stream);
+/* Copy the n = lims[B] results of the last range search to D float32 [n] / I int64 [n] (device pointers if
+ * out_is_device, else host pointers: then the call synchronises `stream`).  PRAG_EINVAL when n does not match. */
+int prag_index_range_result(prag_index_t* ix, float* D, int64_t* I, int64_t n, int out_is_device, void* stream);
+/* Candidates the matrix-core scan of the last range search proposed for the float64 rerank (>= lims[B]; -1: no
+ * range search yet, or it failed). */
+int64_t prag_index_range_candidates(const prag_index_t* ix);
+
 /* The exchange step of the row-sharded index: merge `n_parts` per-shard
  * results (D_parts/I_parts laid out [n_parts, B, k], e.g. straight out of an
  * RCCL all-gather) by (score, id) into the global top-k.  Device pointers. */

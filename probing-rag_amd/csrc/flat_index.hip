@@ -1028,38 +1028,7 @@ __device__ __forceinline__ void rerank_block(const void* __restrict__ rows, int 
     const int nw = blockDim.x >> 6;
     for (int c = w; c < KC; c += nw) {
         const int idx = cand(c);
-        double s = 0.0;
-        if (idx >= 0) {
-            // 8 consecutive elements per lane per step (d is a multiple of 64)
-            for (int e = lane * 8; e < d; e += 512) {
-                float xv[8];
-                if constexpr (F32) {
-                    const f32x4 a0 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(rows) + (int64_t)idx * d + e);
-                    const f32x4 a1 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(rows) + (int64_t)idx * d + e + 4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { xv[j] = a0[j]; xv[4 + j] = a1[j]; }
-                } else {
-                    const half8 h = *reinterpret_cast<const half8*>(reinterpret_cast<const _Float16*>(rows) + (int64_t)idx * d + e);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) xv[j] = (float)h[j];
-                }
-                const f32x4 q0 = *reinterpret_cast<const f32x4*>(q + e);
-                const f32x4 q1 = *reinterpret_cast<const f32x4*>(q + e + 4);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const double qv = (double)(j < 4 ? q0[j] : q1[j - 4]);
-                    const double x = (double)xv[j];
-                    if (metric_l2) {
-                        const double t = qv - x;
-                        s = fma(t, t, s);
-                    } else {
-                        s = fma(qv, x, s);
-                    }
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        }
+        const double s = idx >= 0 ? row_score64<F32>(rows, d, metric_l2, q, idx, lane) : 0.0;
         if (lane == 0) {
             s_score[c] = s;
             s_idx[c] = idx;
@@ -1397,17 +1366,38 @@ static bool shadow_wanted(prag_index* ix) {
     return true;
 }
 
-// Bring the shadow up to date with the stored rows (allocation follows the row capacity; rows added since
-// the last call are quantised; the max ||x||^2 word the shadow's error constants read is refreshed).
-// Called at the end of every add (so that no search pays for it), from prag_index_prepare, and - a no-op
-// then - from the search itself.
-static int shadow_ensure(prag_index* ix, hipStream_t st) {
+// max ||x||^2 over the rows (cert_words[1]) brought up to date with the rows added since the last refresh
+int index_refresh_xn_max(prag_index* ix, hipStream_t st) {
     if (ix->xn_max_rows < ix->ntotal) {  // rows added since the last refresh
         const int blocks = (int)std::min<int64_t>(1024, (ix->ntotal - ix->xn_max_rows + 255) / 256);
         hipLaunchKernelGGL(xnorm_max_kernel, dim3(blocks), dim3(256), 0, st, ix->xnorm, ix->xn_max_rows, ix->ntotal,
                            ix->cert_words + 1);
         PRAG_LAUNCH_CHECK();
         ix->xn_max_rows = ix->ntotal;
+    }
+    return PRAG_OK;
+}
+
+// prep_queries_kernel of a search without any of its selection state (the range search, flat_range.hip)
+int index_prep_queries(const prag_index* ix, const float* q_dev, int B, int Bpad, float* q32, _Float16* q16,
+                       _Float16* q16lo, float* qinfo, double* qn2, uint32_t* g_tau, uint32_t* g_slot, uint32_t* n_flag,
+                       hipStream_t st) {
+    const ShadowPrep none{};
+    hipLaunchKernelGGL(prep_queries_kernel, dim3((Bpad + 3) / 4, 1), dim3(256), 0, st, q_dev, B, Bpad, ix->d,
+                       ix->metric == PRAG_METRIC_COS ? 1 : 0, q32, q16, q16lo, g_tau, nullptr, nullptr, 0u, qinfo, qn2,
+                       n_flag, nullptr, 0, g_slot, none, Gate{});
+    PRAG_LAUNCH_CHECK();
+    return PRAG_OK;
+}
+
+// Bring the shadow up to date with the stored rows (allocation follows the row capacity; rows added since
+// the last call are quantised; the max ||x||^2 word the shadow's error constants read is refreshed).
+// Called at the end of every add (so that no search pays for it), from prag_index_prepare, and - a no-op
+// then - from the search itself.
+static int shadow_ensure(prag_index* ix, hipStream_t st) {
+    {
+        const int rc = index_refresh_xn_max(ix, st);
+        if (rc != PRAG_OK) return rc;
     }
     if (!shadow_wanted(ix)) {
         if ((ix->shadow_no_room || ix->shadow_failed) && ix->rows8) {   // an undersized shadow nobody will read again
@@ -3110,6 +3100,7 @@ extern "C" int prag_index_profile_read(prag_index_t* ix, float* ms, int cap, int
 
 extern "C" void prag_index_destroy(prag_index_t* ix) {
     if (!ix) return;
+    range_state_free(ix);
     ix->prof.disable();
     ix->prof_xch.disable();
     if (ix->scan_done_ev) (void)hipEventDestroy(ix->scan_done_ev);

@@ -226,6 +226,7 @@ struct prag_index {
     TailGate* tail = nullptr;   // prag_search_and_gate: the gate launch the running search may carry beside its bound kernel
     int last_flagged = -1;   // flag count of the last host-io search (-1: last search was device-io)
     std::string last_plan;   // plan_describe of the most recent search (prag_index_last_plan)
+    struct RangeState* range = nullptr;   // workspaces and results of the last range search (flat_range.hip)
     EventRing prof;
 };
 
@@ -260,6 +261,15 @@ inline int ws_regrow(std::initializer_list<WsItem> items) {
 template <typename T>
 inline void** vpp(T** p) { return reinterpret_cast<void**>(p); }
 
+
+// pieces of the search the range search (flat_range.hip) shares: max ||x||^2 brought up to date (cert_words[1]), and
+// prep_queries_kernel into the caller's buffers (q32 [B][d], q16 / q16lo [Bpad][d], qinfo [Bpad][4], qn2 [Bpad];
+// g_tau [Bpad], g_slot [Bpad][kSlotWordsFwd] and one n_flag word are written and not needed)
+int index_refresh_xn_max(prag_index* ix, hipStream_t st);
+int index_prep_queries(const prag_index* ix, const float* q_dev, int B, int Bpad, float* q32, _Float16* q16,
+                       _Float16* q16lo, float* qinfo, double* qn2, uint32_t* g_tau, uint32_t* g_slot, uint32_t* n_flag,
+                       hipStream_t st);
+void range_state_free(prag_index* ix);
 
 // prag_index_search's body (flat_index.hip): tag_ids = ids in the exchange format of a row shard
 int index_search_impl(prag_index_t* ix, const float* q, int B, int k, int64_t id_offset, float* D, int64_t* I, int io_is_device,

@@ -216,6 +216,45 @@ __device__ __forceinline__ double cert_eps(const CertArgs& c, int b, int metric_
     return metric_l2 ? 2.0 * eps_dot + 2.384185791015625e-07 * (xn + 2.0 * nq * nx) : eps_dot;
 }
 
+// The float64 score of stored row idx against the query q as the rerank uses it (f32, normalised for cosine), one
+// wave: 8 consecutive elements per lane per step (d is a multiple of 64), then a butterfly sum; every lane returns
+// the total.  Every result D of a search and of a range search is (float) of this value, so this summation order
+// IS the definition of D: do not change it.
+template <bool F32>
+__device__ __forceinline__ double row_score64(const void* __restrict__ rows, int d, int metric_l2,
+                                              const float* __restrict__ q, int64_t idx, int lane) {
+    double s = 0.0;
+    for (int e = lane * 8; e < d; e += 512) {
+        float xv[8];
+        if constexpr (F32) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(rows) + idx * d + e);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(rows) + idx * d + e + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { xv[j] = a0[j]; xv[4 + j] = a1[j]; }
+        } else {
+            const half8 h = *reinterpret_cast<const half8*>(reinterpret_cast<const _Float16*>(rows) + idx * d + e);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xv[j] = (float)h[j];
+        }
+        const f32x4 q0 = *reinterpret_cast<const f32x4*>(q + e);
+        const f32x4 q1 = *reinterpret_cast<const f32x4*>(q + e + 4);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const double qv = (double)(j < 4 ? q0[j] : q1[j - 4]);
+            const double x = (double)xv[j];
+            if (metric_l2) {
+                const double t = qv - x;
+                s = fma(t, t, s);
+            } else {
+                s = fma(qv, x, s);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    return s;
+}
+
 // true = the k best of the candidates are provably the k best of the shard
 __device__ __forceinline__ bool cert_ok(const CertArgs& c, int b, int metric_l2, double kth_exact_score,
                                         float kth_sel) {

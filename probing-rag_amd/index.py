@@ -117,6 +117,43 @@ class HipFlatIndex:
         del keep
         return D, I
 
+    def range_search(self, x, radius: float, id_offset: int = 0):
+        """faiss ``index.range_search(x, radius)`` -> (lims int64 [B+1], D float32 [n], I int64 [n]), n = lims[B].
+        Results of query b: entries [lims[b], lims[b+1]) in ascending row id; L2: every row with squared distance
+        < radius, IP / COS: every row with score > radius (exact, float64 scores; D bit-identical to search's).
+        ``lims`` is always a NumPy array (the call synchronises); D / I are NumPy arrays for host queries and tensors
+        on the index's device for device queries."""
+        import torch
+        dev_io = isinstance(x, torch.Tensor) and x.is_cuda
+        if dev_io and x.device != self.device:
+            raise ValueError(f"queries on {x.device}, index on {self.device}")
+        ptr, B, _, keep = self._rows_arg(x)
+        lims = np.zeros(B + 1, np.int64)
+        if B == 0:
+            empty = (torch.empty(0, dtype=torch.float32, device=self.device), torch.empty(0, dtype=torch.int64, device=self.device)) \
+                if dev_io else (np.empty(0, np.float32), np.empty(0, np.int64))
+            return (lims,) + empty
+        with torch.cuda.device(self.device):
+            stream = _lib.current_stream_ptr(self.device)
+            _lib.check(_lib.lib().prag_index_range_search(self._h, ptr, B, float(radius), int(id_offset),
+                                                          ctypes.c_void_p(lims.ctypes.data), 1 if dev_io else 0, stream))
+            n = int(lims[B])
+            if dev_io:
+                D = torch.empty(n, dtype=torch.float32, device=self.device)
+                I = torch.empty(n, dtype=torch.int64, device=self.device)
+                dp, ip = D.data_ptr(), I.data_ptr()
+            else:
+                D, I = np.empty(n, np.float32), np.empty(n, np.int64)
+                dp, ip = D.ctypes.data, I.ctypes.data
+            _lib.check(_lib.lib().prag_index_range_result(self._h, ctypes.c_void_p(dp), ctypes.c_void_p(ip), n,
+                                                          1 if dev_io else 0, stream))
+        del keep
+        return lims, D, I
+
+    def range_candidates(self) -> int:
+        """Rows the matrix-core scan of the last range_search proposed for the float64 rerank (-1: none yet)."""
+        return int(_lib.lib().prag_index_range_candidates(self._h))
+
     # ---- row-sharded search through the C-level exchange (prag_index_set_comm / prag_index_search_sharded) ----
     def set_comm(self, comm_ptr, rank: int, world: int):
         """Hand the index an RCCL communicator (an ncclComm_t as an integer / c_void_p; None with world 1)."""

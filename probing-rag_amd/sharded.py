@@ -59,6 +59,12 @@ class HipEngine:
             q = q.to(self.device)
         return self.index.search(q, k, id_offset=id_offset)
 
+    def range_search(self, q, radius, id_offset):
+        q = torch.as_tensor(q)
+        if not q.is_cuda:
+            q = q.to(self.device)
+        return self.index.range_search(q, radius, id_offset=id_offset)
+
     def merge(self, D_parts, I_parts, k, metric):
         from .index import merge_topk
         return merge_topk(D_parts, I_parts, k, metric)
@@ -261,6 +267,55 @@ class ShardedFlatIndex:
         self.dist.all_gather_into_tensor(D_all, D_loc.contiguous(), group=self.group)
         self.dist.all_gather_into_tensor(I_all, I_loc.contiguous(), group=self.group)
         return self.engine.merge(D_all.view(self.world, B, k), I_all.view(self.world, B, k), k, self.metric)
+
+
+    def range_search(self, q, radius: float):
+        """q replicated on every rank -> identical (lims int64 [B+1], D float32 [n], I int64 [n]) on every rank: each
+        rank range-searches its contiguous shard with its global id offset; the per-query counts are all-gathered
+        ([world, B]), then the results, padded to the largest total; segments are concatenated in rank order, which
+        keeps the ascending global ids (shards are contiguous and ascending) without a sort.  lims is a NumPy array."""
+        import numpy as np
+        if not self._synced:
+            raise RuntimeError("ShardedFlatIndex.sync() must run (on every rank) after adding rows")
+        lims, D, I = self.engine.range_search(q, radius, self.id_offset)
+        lims = np.asarray(lims, dtype=np.int64)
+        B = len(lims) - 1
+        dev = getattr(self.engine, "device", torch.device("cpu"))
+        D = torch.as_tensor(D).to(dev)
+        I = torch.as_tensor(I).to(dev)
+        if self.world == 1:
+            return lims, D, I
+        counts = torch.from_numpy(np.diff(lims)).to(dev)
+        # (concatenated-along-dim-0 outputs: valid on both RCCL and gloo)
+        all_counts = torch.empty(self.world * B, dtype=torch.int64, device=dev)
+        self.dist.all_gather_into_tensor(all_counts, counts.contiguous(), group=self.group)
+        all_counts = all_counts.cpu().numpy().reshape(self.world, B)
+        totals = all_counts.sum(axis=1)
+        m = int(totals.max())
+        out_lims = np.zeros(B + 1, np.int64)
+        out_lims[1:] = np.cumsum(all_counts.sum(axis=0))
+        if m == 0:
+            return out_lims, D[:0], I[:0]
+        Dp = torch.zeros(m, dtype=torch.float32, device=dev)
+        Ip = torch.zeros(m, dtype=torch.int64, device=dev)
+        Dp[:D.numel()] = D
+        Ip[:I.numel()] = I
+        D_all = torch.empty(self.world * m, dtype=torch.float32, device=dev)
+        I_all = torch.empty(self.world * m, dtype=torch.int64, device=dev)
+        self.dist.all_gather_into_tensor(D_all, Dp, group=self.group)
+        self.dist.all_gather_into_tensor(I_all, Ip, group=self.group)
+        # query b: rank 0's segment, rank 1's, ... (one gather index over the [world, m] blocks)
+        starts = np.zeros((self.world, B + 1), np.int64)
+        starts[:, 1:] = np.cumsum(all_counts, axis=1)
+        src = np.empty(int(out_lims[B]), np.int64)
+        pos = 0
+        for b in range(B):
+            for r in range(self.world):
+                c = int(all_counts[r, b])
+                src[pos:pos + c] = r * m + starts[r, b] + np.arange(c)
+                pos += c
+        src_t = torch.from_numpy(src).to(dev)
+        return out_lims, D_all[src_t], I_all[src_t]
 
 
 def _sharded_search_and_gate(self, q, k: int, ens, x, ablation: int = 0, threshold: float = 0.0, gate_out=None):
