@@ -323,6 +323,32 @@ int prag_index_range_result(prag_index_t* ix, float* D, int64_t* I, int64_t n, i
  * range search yet, or it failed). */
 int64_t prag_index_range_candidates(const prag_index_t* ix);
 
+/* Exact filtered search (faiss `index.search(x, k, params=SearchParameters(sel=...))`): the k best rows of the
+ * selected subset S, as search would rank them if the index held only the rows of S.
+ *   Ranking by s64 (the float64 score of range search above), ascending for L2, descending for IP / COS, ties by the
+ *   lower id; D = float32(s64), I = row + id_offset; faiss padding (-1, +FLT_MAX for L2 / -FLT_MAX for IP and COS) when
+ *   fewer than k stored rows are selected.  With every row selected the result equals search's bit for bit.
+ *   allow: uint32 words, bit (i & 31) of word (i >> 5) = local row i is selected (= faiss IDSelectorBitmap's bytes on a
+ *   little-endian host, padded to 4 B).  n_words >= ceil(ntotal / 32), else PRAG_EINVAL; bits at or past ntotal are
+ *   ignored.  allow_is_device: device or host pointer.  Other arguments and limits as prag_index_search
+ *   (1 <= k <= 911); 0 <= B <= 1024 (B = 0 writes nothing, as search).  One selector applies to every query.
+ *   Two exact paths, chosen ON THE DEVICE by the kernel that compacts the bitmap (both are always enqueued and
+ *   switched by a word it writes): 1 = the direct scan over the 32-row tiles holding a selected row, unselected rows
+ *   masked out, float64 rerank and certificate as search; 2 = float64 brute force over the list of selected rows (every
+ *   k > 26, small selections, and the queries the certificate of path 1 could not clear).  PRAG_FILTER_PATH=1|2 pins
+ *   the path (k > 26 always takes 2).  With io_is_device the call does not synchronise the host; otherwise it copies in
+ *   and out and synchronises `stream`.  Reads the stored rows (never the 8-bit shadow) and leaves every state of
+ *   search as it was (bounds, workgroup tuning, prag_index_last_plan, tier statistics).  No tagged ids, no C-level
+ *   sharded form: ShardedFlatIndex.search(q, k, params) exchanges through torch.distributed. */
+int prag_index_search_filtered(prag_index_t* ix, const float* q, int B, int k, int64_t id_offset,
+                               const uint32_t* allow, int64_t n_words, int allow_is_device,
+                               float* D, int64_t* I, int io_is_device, void* stream);
+/* Measurement hook of the last filtered search (synchronises stream): rows selected, 32-row tiles holding at least
+ * one selected row, the path that ran (1 masked scan, 2 gathered float64), queries the certificate sent to the
+ * gathered path (0 on path 2).  Any output pointer may be NULL.  PRAG_EINVAL before the first filtered search. */
+int prag_index_last_filter(prag_index_t* ix, void* stream, int64_t* n_selected, int64_t* n_tiles, int* path,
+                           int* n_flagged);
+
 /* The exchange step of the row-sharded index: merge `n_parts` per-shard
  * results (D_parts/I_parts laid out [n_parts, B, k], e.g. straight out of an
  * RCCL all-gather) by (score, id) into the global top-k.  Device pointers. */

@@ -81,6 +81,8 @@ SIGNATURES = {
     "prag_index_range_search": (_I, [_P, _P, _I, _F, _L, _P, _I, _P]),
     "prag_index_range_result": (_I, [_P, _P, _P, _L, _I, _P]),
     "prag_index_range_candidates": (_L, [_P]),
+    "prag_index_search_filtered": (_I, [_P, _P, _I, _I, _L, _P, _L, _I, _P, _P, _I, _P]),
+    "prag_index_last_filter": (_I, [_P, _P, ctypes.POINTER(_L), ctypes.POINTER(_L), ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "prag_index_add": (_I, [_P, _P, _L, _I, _P]),
     "prag_index_add_synthetic": (_I, [_P, ctypes.c_uint32, _L, _L]),
     "prag_index_ntotal": (_L, [_P]),

@@ -22,9 +22,7 @@
 
 namespace prag {
 
-constexpr int kExCap = 2048;     // LDS slots per workgroup (k <= 1024 leaves >= 768 free after a cut)
 constexpr int kExCheck = 8;      // row tiles (of 32 rows) between capacity checks
-constexpr int kExThreads = 512;
 
 // Row loads of exact_mfma_kernel: ORDINARY loads.  The float64 scans streamed their rows non-temporally like the first-pass
 // scans since round 4; on THIS kernel's access pattern - 16 B pieces of 16 rows per wave instruction, two adjacent 16 B loads
@@ -37,63 +35,6 @@ __device__ __forceinline__ u32x4 exm_load(const u32x4* p) {
 #else
     return *p;
 #endif
-}
-
-struct ExTopK {
-    unsigned long long key[kExCap];
-    int id[kExCap];
-    unsigned long long bound;    // k-th best key so far (~0: none yet); ties on the key are kept
-    int cnt;
-};
-
-__device__ __forceinline__ void ex_init(ExTopK& t) {
-    if (threadIdx.x == 0) {
-        t.bound = ~0ull;
-        t.cnt = 0;
-    }
-}
-
-__device__ __forceinline__ void ex_push(ExTopK& t, unsigned long long key, int id) {
-    if (key <= t.bound) {
-        const int slot = atomicAdd(&t.cnt, 1);
-        t.key[slot] = key;   // callers keep cnt <= kExCap between cuts
-        t.id[slot] = id;
-    }
-}
-
-// sort the buffered entries by (key, id), keep the k best, tighten the bound.  All threads.
-__device__ __forceinline__ void ex_cut(ExTopK& t, int k) {
-    __syncthreads();
-    const int n = t.cnt;
-    int n_pad = 2;
-    while (n_pad < n) n_pad <<= 1;
-    for (int i = n + threadIdx.x; i < n_pad; i += kExThreads) {
-        t.key[i] = ~0ull;
-        t.id[i] = 0x7fffffff;
-    }
-    for (int size = 2; size <= n_pad; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            __syncthreads();
-            for (int p = threadIdx.x; p < (n_pad >> 1); p += kExThreads) {
-                const int i = ((p / stride) * 2 * stride) + (p % stride), j = i + stride;
-                const unsigned long long ka = t.key[i], kb = t.key[j];
-                const int ia = t.id[i], ib = t.id[j];
-                const bool gt = ka > kb || (ka == kb && ia > ib);
-                if (gt == ((i & size) == 0)) {
-                    t.key[i] = kb;
-                    t.key[j] = ka;
-                    t.id[i] = ib;
-                    t.id[j] = ia;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        t.cnt = n < k ? n : k;
-        if (n >= k) t.bound = t.key[k - 1];
-    }
-    __syncthreads();
 }
 
 struct ExactArgs {

@@ -333,8 +333,11 @@ struct TopList {
 // (~1e-7 relative) instead of the fp16 rounding of the operands (~3e-5): the reference's own call
 // shape (a handful of queries, fp32 rows) no longer depends on how many near-ties surround the
 // k-th result.
-template <int QT, int KC, bool F32, bool HP>
-__device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem) {
+// MASK (filtered search, flat_filter.hip): the waves walk the non-empty tiles of `mt` instead of every tile, and a row
+// whose allow bit is clear gets the key +inf, so it never enters a list (the bounds, the merge, the rerank and the
+// certificate see the selected rows only).  MASK = false is the unfiltered scan, unchanged.
+template <int QT, int KC, bool F32, bool HP, bool MASK = false>
+__device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem, const MaskTiles& mt = MaskTiles{}) {
     static_assert(!HP || QT == 32, "high-precision selection is built for one 32-query tile");
     constexpr int NQ = QT / 32;
     constexpr bool SPLIT_ROWS = HP && F32;          // rows staged as hi + lo halves
@@ -392,7 +395,9 @@ __device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem) {
 
     const int nW = gridDim.x * 8;
     const int gw = blockIdx.x * 8 + w;
-    const int n_my = gw < a.n_tiles ? (a.n_tiles - gw + nW - 1) / nW : 0;
+    // (MASK: tiles are positions in the tile list, the count comes from the compaction kernel)
+    const int n_tiles = MASK ? (int)__builtin_amdgcn_readfirstlane(*mt.count) : a.n_tiles;
+    const int n_my = gw < n_tiles ? (n_tiles - gw + nW - 1) / nW : 0;
 
     TopList<KC> top[NQ];
 #pragma unroll
@@ -441,9 +446,29 @@ __device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem) {
     // NLD offsets cost NLD - 1 registers the 32-deep lists and the float32 rows did not have: scratch).
     const int lane_off0 = st_doc[0] * (int)row_bytes + col_b;
     const int64_t ld_step = (int64_t)(32 / NLD) * row_bytes;
-    const int tile_last = a.n_tiles - 1;
+    const int tile_last = n_tiles - 1;
+    // MASK: list entries (tile, allow word) of list positions m_base + j nW, j = 0..4 (m_base = tile_cur).  The loads
+    // to these positions' row chunks run up to two tiles ahead of tile_cur, so every entry is requested two tiles before
+    // its first use: waiting for it never drains the chunks in flight.
+    // (named scalars, not arrays: a select between array elements became a dynamically indexed load - scratch)
+    [[maybe_unused]] uint32_t m_t0 = 0, m_t1 = 0, m_t2 = 0, m_t3 = 0, m_t4 = 0;   // tiles
+    [[maybe_unused]] uint32_t m_w0 = 0, m_w1 = 0, m_w2 = 0, m_w3 = 0, m_w4 = 0;   // their allow words
+    [[maybe_unused]] int m_base = gw;
+    // (a scalar load: the list is read-only while the scan runs, and the constant address space says so - the entry
+    //  then sits in SGPRs, no VGPRs held for it in flight)
+    [[maybe_unused]] auto m_load = [&](uint32_t& tile, uint32_t& word, int t) {
+        typedef const __attribute__((address_space(4))) unsigned long long* ConstU64;
+        const unsigned long long e = *(ConstU64)(mt.tiles + (t < tile_last ? t : tile_last));
+        tile = (uint32_t)e;
+        word = (uint32_t)(e >> 32);
+    };
     auto issue = [&](u32x4 (&ld)[NLD], int tile, int c) {
-        const int tc = tile < tile_last ? tile : tile_last;     // prefetch past the end: re-read the last tile
+        int tc = tile < tile_last ? tile : tile_last;     // prefetch past the end: re-read the last tile
+        if constexpr (MASK) {       // the entry of list position `tile` (tile_cur, + nW or + 2 nW); a sum of products, not a
+                                    // select between the captured entries: that became a load through a selected address
+            const uint32_t l0 = tile == m_base, l1 = tile == m_base + nW;
+            tc = (int)(m_t0 * l0 + m_t1 * l1 + m_t2 * (1u - l0 - l1));
+        }
         const char* base = rows + (int64_t)tc * (32 * row_bytes) + c * chunk_bytes;
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
@@ -482,9 +507,10 @@ __device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem) {
         // norms of this tile's rows: requested at its first chunk, i.e. OLDER than
         // every prefetch issued below, so waiting for them does not drain the queue
         if (a.use_norm && (ONE_SET ? c_cur == NCH - 1 : c_cur == 0)) {
+            const int tn = MASK ? (int)m_t0 : tile_cur;
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                xn[g] = *reinterpret_cast<const f32x4*>(a.xnorm + (int64_t)tile_cur * 32 + 8 * g + 4 * hh);
+                xn[g] = *reinterpret_cast<const f32x4*>(a.xnorm + (int64_t)tn * 32 + 8 * g + 4 * hh);
         }
 
 #pragma unroll
@@ -536,7 +562,7 @@ __device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem) {
         }
         if (c_cur == NCH - 1) {
             // ---- epilogue: 16 rows x this lane's queries -> running top-KC -------
-            const int64_t doc0 = (int64_t)tile_cur * 32;
+            const int64_t doc0 = (int64_t)(MASK ? (int)m_t0 : tile_cur) * 32;
             float tau[NQ];
 #pragma unroll
             for (int t = 0; t < NQ; ++t) tau[t] = unsortable_f32(s_tau[32 * t + r]);
@@ -545,7 +571,7 @@ __device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int64_t doc = doc0 + 8 * g + 4 * hh + e;
-                    const bool valid = doc < a.N;
+                    const bool valid = MASK ? ((m_w0 >> (8 * g + 4 * hh + e)) & 1u) != 0u : doc < a.N;
 #pragma unroll
                     for (int t = 0; t < NQ; ++t) {
                         const float key = valid ? fmaf(a.alpha, acc[t][4 * g + e], xn[g][e]) : INFINITY;
@@ -607,9 +633,26 @@ __device__ __forceinline__ void scan_topk_body(const ScanArgs& a, char* smem) {
             }
         }
         advance(tile_cur, c_cur);
+        if constexpr (MASK) {
+            if (c_cur == 0) {          // tile_cur moved on: shift the list entries, request the one two tiles out
+                m_base += nW;
+                m_t0 = m_t1; m_t1 = m_t2; m_t2 = m_t3; m_t3 = m_t4;
+                m_w0 = m_w1; m_w1 = m_w2; m_w2 = m_w3; m_w3 = m_w4;
+                m_load(m_t4, m_w4, m_base + 4 * nW);
+            }
+        }
     };
 
     const int n_it = n_my * NCH;
+    if constexpr (MASK) {
+        if (n_it > 0) {
+            m_load(m_t0, m_w0, gw);
+            m_load(m_t1, m_w1, gw + nW);
+            m_load(m_t2, m_w2, gw + 2 * nW);
+            m_load(m_t3, m_w3, gw + 3 * nW);
+            m_load(m_t4, m_w4, gw + 4 * nW);
+        }
+    }
     if constexpr (ONE_SET) {
         if (n_it > 0) {
             issue(ldA, tile_nx, c_nx);
@@ -667,6 +710,15 @@ __global__ __launch_bounds__(512, 1) void scan_topk_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (gate_closed(a.gate)) return;
     scan_topk_body<QT, KC, F32, HP>(a, smem);
+}
+
+// The filtered search's masked scan (flat_filter.hip, path 1): the non-empty tiles of the selection only.  The gate is
+// the path word the compaction kernel wrote.
+template <int QT, int KC, bool F32>
+__global__ __launch_bounds__(512, 1) void scan_topk_masked_kernel(ScanArgs a, MaskTiles mt) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (gate_closed(a.gate)) return;
+    scan_topk_body<QT, KC, F32, false, true>(a, smem, mt);
 }
 
 // Re-run of the query groups (QT queries each) whose candidate buffers overflowed in the
@@ -1766,6 +1818,69 @@ static int launch_merge_rerank(int kc, bool f32, const float* pk, const int* pi,
     }
     PRAG_LAUNCH_CHECK();
     return PRAG_OK;
+}
+
+// ---- the filtered search's masked scan and list merge (flat_filter.hip, path 1) ----
+template <int QT, int KC, bool F32>
+static int launch_masked(const ScanArgs& a, const MaskTiles& mt, int grid, hipStream_t st) {
+    const int lds_loop = QT * a.qstride + 8 * 4096 + QT * 12;
+    const int lds_merge = 16 * 32 * KC * 8;
+    const int lds = lds_loop > lds_merge ? lds_loop : lds_merge;
+    auto kern = scan_topk_masked_kernel<QT, KC, F32>;
+    static LdsOptIn lds_opt_in;
+    {
+        const int rc_ = lds_opt_in.ensure(reinterpret_cast<const void*>(kern), 160 * 1024);
+        if (rc_ != PRAG_OK) return rc_;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, a, mt);
+    PRAG_LAUNCH_CHECK();
+    return PRAG_OK;
+}
+
+// The shapes the filtered search runs (flat_filter.hip filter_masked_shape): fp16 rows with 8- or 16-deep lists on 32- or
+// 64-query tiles, float32 rows with 16- or 32-deep lists on 32-query tiles.  (fp16 rows with 32-deep lists and float32
+// rows on 64-query tiles spill: the tile list's registers on top of the unfiltered kernel's 255 VGPRs.)
+bool index_filter_shape_ok(int QT, int kc, bool f32) {
+    return f32 ? (QT == 32 && (kc == 16 || kc == 32)) : ((QT == 32 || QT == 64) && (kc == 8 || kc == 16));
+}
+
+int index_filter_scan(const prag_index* ix, const FilterScan& f, hipStream_t st) {
+    const int metric_l2 = ix->metric == PRAG_METRIC_L2;
+    ScanArgs a;
+    a.rows = ix->rows;
+    a.xnorm = ix->xnorm;
+    a.q16 = f.q16;
+    a.q16lo = nullptr;
+    a.N = ix->ntotal;
+    a.d = ix->d;
+    a.qstride = f.qstride;
+    a.n_tiles = 0;            // (the tile list's count word)
+    a.alpha = metric_l2 ? -2.0f : -1.0f;
+    a.use_norm = metric_l2;
+    a.out_key = f.part_key;
+    a.out_idx = f.part_idx;
+    a.g_tau = f.g_tau;
+    a.g_slot = f.g_slot;
+    a.gate = f.gate;
+    const bool f32 = ix->store == PRAG_F32;
+    if (f32) {
+        if (f.QT == 32 && f.kc == 16) return launch_masked<32, 16, true>(a, f.mt, f.grid, st);
+        if (f.QT == 32 && f.kc == 32) return launch_masked<32, 32, true>(a, f.mt, f.grid, st);
+    } else {
+        if (f.QT == 32 && f.kc == 8) return launch_masked<32, 8, false>(a, f.mt, f.grid, st);
+        if (f.QT == 32 && f.kc == 16) return launch_masked<32, 16, false>(a, f.mt, f.grid, st);
+        if (f.QT == 64 && f.kc == 8) return launch_masked<64, 8, false>(a, f.mt, f.grid, st);
+        if (f.QT == 64 && f.kc == 16) return launch_masked<64, 16, false>(a, f.mt, f.grid, st);
+    }
+    set_error("internal: masked scan QT=%d KC=%d f32=%d", f.QT, f.kc, (int)f32);
+    return PRAG_EUNSUPPORTED;
+}
+
+int index_merge_rerank(const prag_index* ix, int kc, const float* pk, const int* pi, int n_lists, int QT, int nq, int q0,
+                       const float* q32, int k, int64_t id_offset, float* D, int64_t* I, const CertArgs& cert,
+                       hipStream_t st) {
+    return launch_merge_rerank(kc, ix->store == PRAG_F32, pk, pi, n_lists, QT, nq, q0, ix->rows, ix->d,
+                               ix->metric == PRAG_METRIC_L2, q32, k, id_offset, D, I, cert, st);
 }
 
 // candidates per query of the 8-bit tiled selection: the certificate needs the KC-th selection key to clear the
@@ -3101,6 +3216,7 @@ extern "C" int prag_index_profile_read(prag_index_t* ix, float* ms, int cap, int
 extern "C" void prag_index_destroy(prag_index_t* ix) {
     if (!ix) return;
     range_state_free(ix);
+    filter_state_free(ix);
     ix->prof.disable();
     ix->prof_xch.disable();
     if (ix->scan_done_ev) (void)hipEventDestroy(ix->scan_done_ev);

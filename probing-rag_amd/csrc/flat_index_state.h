@@ -227,6 +227,7 @@ struct prag_index {
     int last_flagged = -1;   // flag count of the last host-io search (-1: last search was device-io)
     std::string last_plan;   // plan_describe of the most recent search (prag_index_last_plan)
     struct RangeState* range = nullptr;   // workspaces and results of the last range search (flat_range.hip)
+    struct FilterState* filter = nullptr; // workspaces and statistics of the last filtered search (flat_filter.hip)
     EventRing prof;
 };
 
@@ -270,6 +271,25 @@ int index_prep_queries(const prag_index* ix, const float* q_dev, int B, int Bpad
                        _Float16* q16lo, float* qinfo, double* qn2, uint32_t* g_tau, uint32_t* g_slot, uint32_t* n_flag,
                        hipStream_t st);
 void range_state_free(prag_index* ix);
+
+// the filtered search (flat_filter.hip): the masked direct scan of one query tile (flat_index.hip scan_topk_masked_kernel)
+// and the list merge + float64 rerank + certificate behind it (merge_rerank_kernel)
+struct FilterScan {
+    int QT, kc, grid, qstride;
+    const _Float16* q16;      // [QT][d] this query tile
+    uint32_t* g_tau;          // [QT]
+    uint32_t* g_slot;         // [QT][kSlotWords] bound slots, or null
+    MaskTiles mt;
+    float* part_key;          // [grid][QT][kc]
+    int* part_idx;
+    Gate gate;
+};
+bool index_filter_shape_ok(int QT, int kc, bool f32);
+int index_filter_scan(const prag_index* ix, const FilterScan& f, hipStream_t st);
+int index_merge_rerank(const prag_index* ix, int kc, const float* pk, const int* pi, int n_lists, int QT, int nq, int q0,
+                       const float* q32, int k, int64_t id_offset, float* D, int64_t* I, const CertArgs& cert,
+                       hipStream_t st);
+void filter_state_free(prag_index* ix);
 
 // prag_index_search's body (flat_index.hip): tag_ids = ids in the exchange format of a row shard
 int index_search_impl(prag_index_t* ix, const float* q, int B, int k, int64_t id_offset, float* D, int64_t* I, int io_is_device,

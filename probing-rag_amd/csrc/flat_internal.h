@@ -270,6 +270,78 @@ __device__ __forceinline__ void cert_flag(const CertArgs& c, int b) {
     c.flag_list[slot] = b;
 }
 
+// Threshold list of the float64 scans in LDS (flat_exact.hip, and the gathered path of the filtered search in
+// flat_filter.hip): entries that can still reach the k best are appended, then sorted and cut to k when it fills.
+#ifdef __HIPCC__
+constexpr int kExCap = 2048;     // LDS slots per workgroup (k <= 1024 leaves >= 768 free after a cut)
+constexpr int kExThreads = 512;
+
+struct ExTopK {
+    unsigned long long key[kExCap];
+    int id[kExCap];
+    unsigned long long bound;    // k-th best key so far (~0: none yet); ties on the key are kept
+    int cnt;
+};
+
+__device__ __forceinline__ void ex_init(ExTopK& t) {
+    if (threadIdx.x == 0) {
+        t.bound = ~0ull;
+        t.cnt = 0;
+    }
+}
+
+__device__ __forceinline__ void ex_push(ExTopK& t, unsigned long long key, int id) {
+    if (key <= t.bound) {
+        const int slot = atomicAdd(&t.cnt, 1);
+        t.key[slot] = key;   // callers keep cnt <= kExCap between cuts
+        t.id[slot] = id;
+    }
+}
+
+// sort the buffered entries by (key, id), keep the k best, tighten the bound.  All threads.
+__device__ __forceinline__ void ex_cut(ExTopK& t, int k) {
+    __syncthreads();
+    const int n = t.cnt;
+    int n_pad = 2;
+    while (n_pad < n) n_pad <<= 1;
+    for (int i = n + threadIdx.x; i < n_pad; i += kExThreads) {
+        t.key[i] = ~0ull;
+        t.id[i] = 0x7fffffff;
+    }
+    for (int size = 2; size <= n_pad; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            __syncthreads();
+            for (int p = threadIdx.x; p < (n_pad >> 1); p += kExThreads) {
+                const int i = ((p / stride) * 2 * stride) + (p % stride), j = i + stride;
+                const unsigned long long ka = t.key[i], kb = t.key[j];
+                const int ia = t.id[i], ib = t.id[j];
+                const bool gt = ka > kb || (ka == kb && ia > ib);
+                if (gt == ((i & size) == 0)) {
+                    t.key[i] = kb;
+                    t.key[j] = ka;
+                    t.id[i] = ib;
+                    t.id[j] = ia;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        t.cnt = n < k ? n : k;
+        if (n >= k) t.bound = t.key[k - 1];
+    }
+    __syncthreads();
+}
+#endif
+
+// The non-empty 32-row tiles of a filtered search (flat_filter.hip filter_compact_kernel), in row order: x = tile
+// index, y = its allow word (bit r: row 32 x + r is selected; bits at or past ntotal are clear).  The masked direct scan
+// (flat_index.hip scan_topk_masked_kernel) walks these tiles only; `count` is a device word.
+struct MaskTiles {
+    const uint2* tiles = nullptr;
+    const uint32_t* count = nullptr;
+};
+
 // Exact fallback: float64 brute force over every row for the flagged queries (flat_exact.hip).
 struct ExactRun {
     const void* rows;       // [N][d] as stored

@@ -90,11 +90,18 @@ class HipFlatIndex:
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().prag_index_add_synthetic(self._h, int(seed) & 0xFFFFFFFF, int(row0), int(n)))
 
-    def search(self, x, k: int, id_offset: int = 0, out=None, tagged: bool = False):
+    def search(self, x, k: int, id_offset: int = 0, out=None, tagged: bool = False, params=None):
         """-> (D float32 [B,k], I int64 [B,k]); -1 / +-FLT_MAX padded if ntotal < k.
         ``out=(D, I)`` lets device callers supply the result tensors.  ``tagged=True`` (row-sharded search
         only): I carries the float32 residual of every score above the row id, for
-        ``merge_topk_packed(..., tagged=True)`` - an exchange format, not ids."""
+        ``merge_topk_packed(..., tagged=True)`` - an exchange format, not ids.
+        ``params=SearchParameters(sel=...)`` (selector.py): the k best of the selected ids only (ids = row + id_offset),
+        exact, as faiss's ``search(x, k, params=...)``; not with ``tagged``."""
+        if params is not None:
+            if tagged:
+                raise ValueError("search: params (an ID selector) and tagged=True cannot be combined")
+            if getattr(params, "sel", None) is not None:
+                return self._search_filtered(x, int(k), int(id_offset), out, params.sel)
         import torch
         k = int(k)
         fn = _lib.lib().prag_index_search_tagged if tagged else _lib.lib().prag_index_search
@@ -116,6 +123,47 @@ class HipFlatIndex:
                           ctypes.c_void_p(I.ctypes.data), 0, _lib.current_stream_ptr(self.device)))
         del keep
         return D, I
+
+    def _search_filtered(self, x, k: int, id_offset: int, out, sel):
+        import torch
+        n = self.ntotal
+        words = sel.window_words(id_offset, n, self.device)
+        if isinstance(words, np.ndarray):
+            words = np.ascontiguousarray(words, dtype=np.uint32)
+            if words.size == 0:
+                words = np.zeros(1, np.uint32)
+            wptr, w_dev = words.ctypes.data, 0
+        else:
+            words = words.to(self.device).contiguous()
+            wptr, w_dev = words.data_ptr(), 1
+        n_words = (n + 31) // 32
+        dev_io = isinstance(x, torch.Tensor) and x.is_cuda
+        if dev_io and x.device != self.device:
+            raise ValueError(f"queries on {x.device}, index on {self.device}")
+        ptr, B, _, keep = self._rows_arg(x)
+        if dev_io:
+            D, I = self._out_arg(out, B, k, x.device)
+            dp, ip = D.data_ptr(), I.data_ptr()
+        else:
+            D, I = np.empty((B, k), np.float32), np.empty((B, k), np.int64)
+            dp, ip = D.ctypes.data, I.ctypes.data
+        with torch.cuda.device(self.device):
+            stream = _lib.current_stream_ptr(self.device)
+            _lib.check(_lib.lib().prag_index_search_filtered(self._h, ptr, B, k, int(id_offset), ctypes.c_void_p(wptr),
+                                                             n_words, w_dev, ctypes.c_void_p(dp), ctypes.c_void_p(ip),
+                                                             1 if dev_io else 0, stream))
+        if w_dev:
+            words.record_stream(torch.cuda.current_stream(self.device))
+        del keep
+        return D, I
+
+    def last_filter(self) -> dict:
+        """The last filtered search (synchronises the current stream): rows selected, 32-row tiles holding one,
+        the path that ran (1 masked scan, 2 gathered float64), queries the certificate sent to the gathered path."""
+        n_sel, n_tiles, path, n_flag = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.lib().prag_index_last_filter(self._h, _lib.current_stream_ptr(self.device), ctypes.byref(n_sel),
+                                                     ctypes.byref(n_tiles), ctypes.byref(path), ctypes.byref(n_flag)))
+        return {"n_selected": n_sel.value, "n_tiles": n_tiles.value, "path": path.value, "n_flagged": n_flag.value}
 
     def range_search(self, x, radius: float, id_offset: int = 0):
         """faiss ``index.range_search(x, radius)`` -> (lims int64 [B+1], D float32 [n], I int64 [n]), n = lims[B].

@@ -53,11 +53,11 @@ class HipEngine:
     def add_synthetic(self, seed, row0, n):
         self.index.add_synthetic(seed, row0, n)
 
-    def search(self, q, k, id_offset):
+    def search(self, q, k, id_offset, params=None):
         q = torch.as_tensor(q)
         if not q.is_cuda:
             q = q.to(self.device)
-        return self.index.search(q, k, id_offset=id_offset)
+        return self.index.search(q, k, id_offset=id_offset, params=params)
 
     def range_search(self, q, radius, id_offset):
         q = torch.as_tensor(q)
@@ -245,10 +245,15 @@ class ShardedFlatIndex:
         self._synced = True
 
     # ---- search ------------------------------------------------------------
-    def search(self, q, k: int):
-        """q replicated on every rank -> identical (D [B,k], I [B,k]) on every rank."""
+    def search(self, q, k: int, params=None):
+        """q replicated on every rank -> identical (D [B,k], I [B,k]) on every rank.
+        ``params=SearchParameters(sel=...)``: the selector is over GLOBAL ids; every rank searches the selected rows of
+        its own window [id_offset, id_offset + n_local) and the per-rank results are exchanged per tensor through
+        torch.distributed and merged (also when the C-level exchange is enabled: it has no filtered form)."""
         if not self._synced:
             raise RuntimeError("ShardedFlatIndex.sync() must run (on every rank) after adding rows")
+        if params is not None and getattr(params, "sel", None) is not None:
+            return self._search_filtered(q, k, params)
         if self._comm is not None:      # local search + ncclAllGather + merge: one C call
             return self.engine.index.search_sharded(q, k, self.id_offset)
         if hasattr(self.engine, "search_packed"):
@@ -268,6 +273,17 @@ class ShardedFlatIndex:
         self.dist.all_gather_into_tensor(I_all, I_loc.contiguous(), group=self.group)
         return self.engine.merge(D_all.view(self.world, B, k), I_all.view(self.world, B, k), k, self.metric)
 
+    def _search_filtered(self, q, k: int, params):
+        D_loc, I_loc = self.engine.search(q, k, self.id_offset, params=params)
+        D_loc, I_loc = torch.as_tensor(D_loc), torch.as_tensor(I_loc)
+        if self.world == 1:
+            return D_loc, I_loc
+        B = D_loc.shape[0]
+        D_all = torch.empty((self.world * B, k), dtype=D_loc.dtype, device=D_loc.device)
+        I_all = torch.empty((self.world * B, k), dtype=I_loc.dtype, device=I_loc.device)
+        self.dist.all_gather_into_tensor(D_all, D_loc.contiguous(), group=self.group)
+        self.dist.all_gather_into_tensor(I_all, I_loc.contiguous(), group=self.group)
+        return self.engine.merge(D_all.view(self.world, B, k), I_all.view(self.world, B, k), k, self.metric)
 
     def range_search(self, q, radius: float):
         """q replicated on every rank -> identical (lims int64 [B+1], D float32 [n], I int64 [n]) on every rank: each
